@@ -2,6 +2,8 @@
 """bench.py -- 6-camera reprojection frames/sec on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --dump-outputs DIR     # + what the last timed step computed, as .npy
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full   # + every check and nested measurement below
     python bench.py --gpus 8 --steps 20 --warmup 5          # starts its 8 ranks itself (torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # ... or is started as one of N ranks (WORLD_SIZE set)
@@ -23,7 +25,16 @@ One STEP of a scene = ClipManager.render_clip("cama"): frame poses for all frame
 float32 cast, float32 inverse) -> cama_pipeline_render (bin -> overlay, one launch each per <= frames-per-call frames).
 value = frames rendered by all ranks / max-over-ranks wall time of the K steps (barrier + synchronize on both sides).
 
-Verification (untimed, BEFORE the timed region): every scene is rendered once on the plain path and hashed
+A plain run does what that figure needs: set up, warm up, time the K steps, write --dump-outputs, print the line (the
+overlay's roofline comes from hipEvents inside the timed steps).  Everything else below -- the verification, the
+`sustained` region, the nested measurements, the projection's roofline, the CPU baselines -- runs with --full only.
+
+--dump-outputs DIR: after the timed steps, the mosaics the last timed step wrote (what a caller of the step receives) go to
+DIR as .npy files: frame_index, mosaic_cell_sums (exact float64 channel sums of every camera cell of every frame) and a fixed,
+seeded float32 sample of the mosaic's bytes (mosaic_sample at mosaic_sample_index); prefixed scene<id>_ when a rank keeps
+several mosaics and rank<r>_ when N > 1.  The inputs are seeded, so the same arguments give the same files on any build.
+
+Verification (--full; untimed, BEFORE the timed region): every scene is rendered once on the plain path and hashed
 (shard.overlay_hash); the per-SCENE hashes travel in the job's single all_gather (RCCL) next to the metrics and rank 0
 compares them with tests/golden/scene_hashes.json -- the hashes of the ORACLE's render of the same scenes
 (tests/golden/gen_scene_hashes.py, CPU) -- so a wrong shard, a scene rendered twice or not at all, or wrong pixels
@@ -32,7 +43,7 @@ overwritten with 0xA5 (Job.poison); after the timed region every rank hashes wha
 buffers and compares it with those verified hashes (exit 3 on a difference) -- which can therefore only pass on bytes the
 timed steps wrote.  CAMA_BENCH_FAULT=skip_overlay (tests) makes the timed steps render nothing and must end in exit 3.
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (`roofline` and `placement` in every run, `placement.unplaced` and the others with --full):
   roofline      dominant kernel = k_overlay, HBM-bound.  achieved = the bytes THAT kernel moves per launch -- every
                 source pixel read once, every mosaic pixel written once: 36*W*H per frame (SURVEY.md 8d's image term) x
                 frames per launch -- / its mean duration measured live with hipEvents on the launch stream
@@ -144,6 +155,15 @@ def parse_args(argv=None):
     ap.add_argument("--sustain-seconds", type=float, default=1.0,
                     help="after the K timed steps, run the same loop for at least this long and report it as "
                          "`sustained` (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the golden-hash verification before and after the timed region, "
+                         "the sustained region, the without-memo / unplaced legs, the projection roofline, the XCD probe, the "
+                         "nested stress (N > 1), reference_default / ingest and the CPU baselines.  Without it a run sets up, "
+                         "warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in the output mosaics as DIR/<name>.npy "
+                         "(float32 / float64, a fixed seeded sample of the uint8 mosaic + exact per-frame, per-camera channel "
+                         "sums + the rendered frame indices; < 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -711,6 +731,51 @@ class Job:
             return [(sid,) + shard.overlay_hash(bufs[k]) for k, (sid, _, _, _) in enumerate(self.scenes)]
         return [(self.scenes[-1][0],) + shard.overlay_hash(self.out)]
 
+    def dump_outputs(self, dirpath, prefix="", n_sample=1 << 21):
+        """--dump-outputs: what the LAST timed step left in this rank's output mosaics (uint8 [F, 2H, 3W, 3]), the buffers a
+        caller of the timed path receives, as .npy files under `dirpath`.  Per mosaic (name prefix + `scene<id>_` when a rank
+        keeps several): frame_index (float64, the image index of every mosaic frame), mosaic_cell_sums (float64 [F, 2, 3, 3]:
+        every camera cell's channel sums, exact), mosaic_sample (float32) of the elements at mosaic_sample_index (float64 flat
+        indices, drawn from a generator of fixed seed: the same positions whenever the shape is the same).  Returns the names."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        if not self.scenes or not self.F:
+            return []
+        if self.batched and self.outs:
+            units = [(sid, cm, buf) for (sid, cm, _, _), buf in zip(self.scenes, self.outs)]
+        else:
+            sid, cm, _, _ = self.scenes[-1]                             # (scenes sharing one buffer: the last one is there)
+            units = [(sid, cm, self.out)]
+        os.makedirs(dirpath, exist_ok=True)
+        names = []
+
+        def save(name, arr):
+            np.save(os.path.join(dirpath, name + ".npy"), arr)
+            names.append(name)
+        for sid, cm, buf in units:
+            p = prefix + (f"scene{sid}_" if len(units) > 1 else "")
+            F, H2, W3, C = (int(v) for v in tuple(buf.shape))
+            spans = buf.spans() if hasattr(buf, "spans") else [(0, F, buf)]
+            idx_all, _ = cm.frame_poses("cama")
+            save(p + "frame_index", np.asarray(idx_all[self.lo:self.hi] if self.frame_range is not None else idx_all, np.float64))
+            sums = np.zeros((F, 2, 3, C), np.float64)
+            for lo, hi, t in spans:
+                for f in range(hi - lo):
+                    cell = t[f].reshape(2, H2 // 2, 3, W3 // 3, C).sum(dim=(1, 3), dtype=torch.int64)
+                    sums[lo + f] = cell.cpu().numpy()
+            save(p + "mosaic_cell_sums", sums)
+            per = H2 * W3 * C
+            at = np.sort(np.random.default_rng(0).integers(0, F * per, min(max(1, n_sample // len(units)), F * per)))
+            vals = np.empty(at.size, np.float32)
+            for lo, hi, t in spans:
+                sel = (at >= lo * per) & (at < hi * per)
+                if sel.any():
+                    pos = torch.from_numpy(at[sel] - lo * per).to(t.device)
+                    vals[sel] = t.reshape(-1)[pos].float().cpu().numpy()
+            save(p + "mosaic_sample", vals)
+            save(p + "mosaic_sample_index", at.astype(np.float64))
+        return names
+
     def frames_per_launch(self):
         if not self.scenes or not self.F:
             return 0.0
@@ -1083,12 +1148,14 @@ def main():
     stagger_allocate(job, rank, world, sync_all)
     key = args_key(args, unit="frame" if args.shard_frames else "scene")
     samples = stress_sample_frames(args.frames) if args.shard_frames else None
-    # verification first (untimed): every scene rendered once on the plain single-stream path and hashed -- what the timed
-    # region then repeats is known to be right before it is timed
-    hashes = [] if args.no_verify else job.scene_hashes(samples)
+    full = args.full
+    verify = full and not args.no_verify
+    # verification first (untimed, --full): every scene rendered once on the plain single-stream path and hashed -- what the
+    # timed region then repeats is known to be right before it is timed
+    hashes = job.scene_hashes(samples) if verify else []
     dt, ov_ms, ov_n = job.run(args.steps, args.warmup, sync_all, prof_every)
     N, F = job.N, job.F
-    if not args.no_verify and args.steps > 0:
+    if verify and args.steps > 0:
         # the bytes the timed path wrote must be the bytes that were verified before it (plain path): compared on this rank
         want = {u: (lo, hi) for u, lo, hi in hashes}
         bad = [u for u, lo, hi in job.timed_output_hashes(samples) if want.get(u) != (lo, hi)]
@@ -1096,11 +1163,13 @@ def main():
             print(f"bench.py: rank {rank}: the timed path's output differs from the verified render for units {bad}",
                   file=sys.stderr, flush=True)
             sys.exit(3)
-    sus_steps, sus_dt = job.sustain(args.sustain_seconds, args.steps, dt, sync_all)
-    unmemoised = job.unmemoised_leg(args.steps, args.warmup, sync_all) if (world == 1 and args.steps > 0) else None
+    if args.dump_outputs and args.steps > 0:
+        job.dump_outputs(args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "", n_sample=(1 << 21) // world)
+    sus_steps, sus_dt = job.sustain(args.sustain_seconds, args.steps, dt, sync_all) if full else (0, 0.0)
+    unmemoised = job.unmemoised_leg(args.steps, args.warmup, sync_all) if (full and world == 1 and args.steps > 0) else None
     unplaced = job.unplaced_leg(args.steps, args.warmup, sync_all, prof_every) \
-        if (world == 1 and args.steps > 0 and os.environ.get("CAMA_AUDITION", "16") != "0") else None
-    vbytes, sbytes, bin_stats = job.projection_bytes()
+        if (full and world == 1 and args.steps > 0 and os.environ.get("CAMA_AUDITION", "16") != "0") else None
+    vbytes, sbytes, bin_stats = job.projection_bytes() if full else (0.0, 0.0, None)
     metrics = [float(F * args.steps * len(job.scenes)), dt, ov_ms, float(ov_n), float(N),
                float(args.steps) * len(job.scenes) * shard.scene_cost(F, N, W, H), job.frames_per_launch(), 0.0,
                job.project_ms, float(job.project_n), vbytes, sbytes,
@@ -1115,7 +1184,8 @@ def main():
     report = [shard.pack_report(metrics, hashes, slots)]
 
     # ---------------------------------------------------------------- nested stress (configs[4]), N > 1 default only
-    do_stress = world > 1 and not args.no_stress and not args.shard_frames and args.scenes == 0 and args.map == "lanes"
+    do_stress = (full and world > 1 and not args.no_stress and not args.shard_frames and args.scenes == 0
+                 and args.map == "lanes")
     if do_stress:
         job.free()
         cm0 = frames0 = None
@@ -1128,9 +1198,9 @@ def main():
         stagger_allocate(sjob, rank, world, sync_all)
         s_steps, s_warm = max(1, args.steps // 4), max(1, args.warmup // 4)
         s_samples = stress_sample_frames(sargs.frames)
-        s_hashes = [] if args.no_verify else sjob.scene_hashes(s_samples)
+        s_hashes = sjob.scene_hashes(s_samples) if verify else []
         sdt, sov_ms, sov_n = sjob.run(s_steps, s_warm, sync_all, prof_every)
-        if not args.no_verify:
+        if verify:
             want = {u: (lo, hi) for u, lo, hi in s_hashes}
             bad = [u for u, lo, hi in sjob.timed_output_hashes(s_samples) if want.get(u) != (lo, hi)]
             if bad:
@@ -1158,7 +1228,7 @@ def main():
             agg = shard.reduce_metrics(m)
             golden = shard.load_golden_hashes(GOLDEN_SCENES, golden_key)
             check = None
-            if not args.no_verify:
+            if verify:
                 check = shard.verify_hashes(found, golden, expect_units)
                 check["golden"] = f"tests/golden/scene_hashes.json[{golden_key!r}]" if golden else None
                 check["units"] = what
@@ -1233,16 +1303,22 @@ def main():
             "roofline_project": r_project,
             "scratch_bytes": int(m[0, 18]),
         }
+        if not full:
+            # the projection's bytes (and with them its roofline and the whole-step figures) come from an extra render
+            for k in ("hbm_GBps_whole_step", "hbm_frac_whole_step", "roofline_project"):
+                line.pop(k)
         if args.raw_frames:
             line["config"]["workload"] += "; raw 1600x900 frames resampled on device each step"
             # this mode's kernel reads the raw frames and writes the resized mosaic: 3*C*(H0*W0 + H*W) bytes per frame
             raw_image = 3 * 6 * (900 * 1600 + H * W)
             r_overlay, r_project, raw_bytes = rooflines(m, raw_image, "k_overlay_raw*")
             r_overlay["bytes_per_frame"] = "3*C*(H0*W0 + H*W): raw frame read once, resized mosaic written once"
-            line["roofline"], line["roofline_project"] = r_overlay, r_project
-            bytes_per_frame = raw_bytes
-            line["hbm_GBps_whole_step"] = raw_bytes * (float(m[0, 0]) / float(m[0, 1])) / 1e9
-            line["hbm_frac_whole_step"] = line["hbm_GBps_whole_step"] / HBM_PEAK_GBS
+            line["roofline"] = r_overlay
+            if full:
+                line["roofline_project"] = r_project
+                bytes_per_frame = raw_bytes
+                line["hbm_GBps_whole_step"] = raw_bytes * (float(m[0, 0]) / float(m[0, 1])) / 1e9
+                line["hbm_frac_whole_step"] = line["hbm_GBps_whole_step"] / HBM_PEAK_GBS
         sus_frames, sus_secs = float(m[:, 12].sum()), float(m[:, 13].max())
         if sus_secs > 0:
             line["sustained"] = {"value": sus_frames / sus_secs, "unit": "frames/s", "seconds": sus_secs,
@@ -1280,11 +1356,12 @@ def main():
                                  "note": "rows per band of the overlay, chosen per launch by the pipeline: 8 instead of 4 once the same map's "
                                          "earlier launches have shown >= 0.045 band entries per destination pixel (dense maps)"}
         try:
-            periodic, first8, per_xcd = job.eng.xcd_map()
-            line["xcd_dispatch"] = {"round_robin_over_8_xcds": periodic, "xcd_of_blocks_0_to_7": first8,
-                                    "blocks_per_xcd": per_xcd,
-                                    "note": "the overlay's XCD-contiguous mapping assumes consecutive blocks go round-robin "
-                                            "over the 8 XCDs (speed only; HW_REG_XCC_ID probe)"}
+            if full:                                                # (a probe launch of its own)
+                periodic, first8, per_xcd = job.eng.xcd_map()
+                line["xcd_dispatch"] = {"round_robin_over_8_xcds": periodic, "xcd_of_blocks_0_to_7": first8,
+                                        "blocks_per_xcd": per_xcd,
+                                        "note": "the overlay's XCD-contiguous mapping assumes consecutive blocks go round-robin "
+                                                "over the 8 XCDs (speed only; HW_REG_XCC_ID probe)"}
         except Exception as e:
             line["xcd_dispatch"] = {"error": repr(e)}
         try:
@@ -1365,7 +1442,7 @@ def main():
             sys.exit(3)                                          # a wrong render never prints a throughput line
         default_workload = (world == 1 and n_scenes == 1 and args.map == "lanes" and not args.raw_frames and not args.shard_frames
                             and (W, H) == (1600, 900) and not _segments(args) and not args.no_extras and not args.no_verify)
-        if default_workload:
+        if full and default_workload:
             # the reference's default pipeline and its ingest stage, in the line the driver records
             line["reference_default"], ok = reference_default_leg(device, sync_all, prof_every)
             if not ok:
@@ -1379,7 +1456,7 @@ def main():
         if failures:
             print("\n".join(failures), file=sys.stderr, flush=True)
             sys.exit(3)
-        if world == 1 and args.cpu_seconds > 0 and not args.raw_frames and cm0 is not None:
+        if full and world == 1 and args.cpu_seconds > 0 and not args.raw_frames and cm0 is not None:
             line["cpu_baseline"] = cpu_baseline(cm0, frames0, clip0, args, args.cpu_seconds)
             line["speedup_vs_cpu_baseline"] = fps / line["cpu_baseline"]["value"]
             if args.cpu_pool_seconds > 0 and args.map == "lanes":

@@ -55,3 +55,11 @@ def test_segment_modes_and_workload_keys():
     keys = {bench.args_key(bench.parse_args(a)) for a in ([], ["--segments"], ["--segments", "--wu"])}
     assert len(keys) == 3
     assert bench._segments(bench.parse_args(["--segments", "--wu"])) == "wu" and bench._segments(bench.parse_args(["--segments"])) is True
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"

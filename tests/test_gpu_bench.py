@@ -4,7 +4,9 @@
     GPU, so the two ranks share it (CAMA_BENCH_SHARE_GPU=1 -> gloo for the one collective: RCCL refuses two ranks on one
     device); what is checked is the N > 1 code path: sharding, the all_gather, the per-scene hash check.
   * the N = 1 line: no roofline fraction above 1 on a map where the vertex term matters, the
-    projection has its own roofline object, a sustained figure and the CPU baselines are present.
+    projection has its own roofline object, a sustained figure and the CPU baselines are present (all with --full).
+  * a plain run (no --full) times exactly the K steps and carries only the headline; --dump-outputs writes the last timed
+    step's mosaics, the same bytes from run to run and the bytes the oracle renders.
 """
 import json
 import os
@@ -30,7 +32,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     env = {"CAMA_BENCH_SHARE_GPU": "1"}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         os.environ.pop(k, None)
-    p, line = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], env)
+    p, line = _run(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1"], env)
     assert p.returncode == 0, p.stderr[-3000:]
     assert line is not None, p.stdout[-2000:]
     assert line["n_gpus"] == 2 and line["rccl_world"] == 2
@@ -67,7 +69,7 @@ def test_bench_gpus_beyond_the_node_is_refused_not_asserted():
 def test_bench_line_site_map_roofline_is_attributed_per_kernel():
     """A site-sized map (~3e5 vertices over the 600 m extent): the overlay is charged its image bytes only, the
     projection its own (culled) vertex bytes -- no fraction above 1 anywhere, whole-step below the kernel figures."""
-    p, line = _run(["--map", "site", "--verts", "300000", "--frames", "16", "--steps", "6", "--warmup", "2",
+    p, line = _run(["--full", "--map", "site", "--verts", "300000", "--frames", "16", "--steps", "6", "--warmup", "2",
                     "--cpu-seconds", "0", "--no-verify", "--sustain-seconds", "0.3"])
     assert p.returncode == 0, p.stderr[-3000:]
     ro, rp = line["roofline"], line["roofline_project"]
@@ -81,7 +83,7 @@ def test_bench_line_site_map_roofline_is_attributed_per_kernel():
 
 
 def test_bench_default_line_has_every_contract_field():
-    p, line = _run(["--steps", "20", "--warmup", "5", "--cpu-seconds", "3", "--cpu-pool-seconds", "2", "--cpu-workers", "4"])
+    p, line = _run(["--full", "--steps", "20", "--warmup", "5", "--cpu-seconds", "3", "--cpu-pool-seconds", "2", "--cpu-workers", "4"])
     assert p.returncode == 0, p.stderr[-3000:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -124,7 +126,7 @@ def test_bench_default_line_has_every_contract_field():
 def test_bench_timed_path_that_renders_nothing_is_caught():
     """the output buffers are poisoned between the warm-up and the timed region, so the hash check after
     it can only pass on bytes the timed steps wrote.  Fault injection: the timed steps render nothing -> exit 3, no line."""
-    args = ["--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--sustain-seconds", "0", "--no-extras"]
+    args = ["--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--sustain-seconds", "0", "--no-extras"]
     p, line = _run(args, {"CAMA_BENCH_FAULT": "skip_overlay"}, timeout=600)
     assert p.returncode == 3 and line is None, (p.returncode, p.stdout[-500:], p.stderr[-1500:])
     assert "timed path's output differs" in p.stderr
@@ -138,7 +140,7 @@ def test_bench_timed_path_that_renders_nothing_is_caught():
 
 def test_bench_frame_sharded_timed_path_is_checked_too():
     """The frame-sharded (stress-shaped) job: same poison + fault, on the sampled frame positions."""
-    args = ["--map", "random", "--verts", "200000", "--frames", "48", "--shard-frames", "--height", "180", "--width", "320",
+    args = ["--full", "--map", "random", "--verts", "200000", "--frames", "48", "--shard-frames", "--height", "180", "--width", "320",
             "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--sustain-seconds", "0"]
     p, line = _run(args, {"CAMA_BENCH_FAULT": "skip_overlay"}, timeout=600)
     assert p.returncode == 3 and line is None, (p.returncode, p.stderr[-1500:])
@@ -151,8 +153,46 @@ def test_bench_one_rank_rccl_group():
     (init with device_id, barrier, the int64 all_gather_into_tensor of the report) on the box's one GPU."""
     env = {"CAMA_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29517", "RANK": "0", "WORLD_SIZE": "1",
            "LOCAL_RANK": "0", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}
-    p, line = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--sustain-seconds", "0", "--no-extras"], env,
+    p, line = _run(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--sustain-seconds", "0", "--no-extras"], env,
                    timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert line["rccl_world"] == 1 and "RCCL" in line["collective"], line["collective"]
     assert line["hash_check"]["verified"] == 1
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_steps_mosaics(tmp_path):
+    """A plain run (no --full): the headline fields over exactly the K timed steps and none of --full's figures.
+    --dump-outputs: the last timed step's mosaic, float32 / float64 files under 64 MB, the same files from run to run, and
+    the bytes the oracle renders for the same seeded scene (the small twin of tests/golden/scene_hashes.json)."""
+    import numpy as np
+    import bench
+    from tests.golden import gen_scene_hashes as G
+    argv = ["--verts", "3000", "--frames", "6", "--height", "180", "--width", "320", "--steps", "3", "--warmup", "1"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        p, line = _run(argv + ["--dump-outputs", str(d)], timeout=600)
+        assert p.returncode == 0 and line is not None, p.stderr[-3000:]
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert line["unit"] == "frames/s" and line["metric"] == "6-cam frames/sec (320x180)"
+        assert abs(line["value"] - 3 * 6 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+        for key in ("sustained", "without_memo", "roofline_project", "cpu_baseline", "reference_default", "ingest",
+                    "xcd_dispatch", "projection_stats"):
+            assert key not in line, key
+        assert line["hash_check"] is None and "unplaced" not in line["placement"]
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert set(files) == {"frame_index.npy", "mosaic_cell_sums.npy", "mosaic_sample.npy", "mosaic_sample_index.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        dumps.append(files)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+    a = bench.parse_args(argv)
+    xyz, col, cams, w2c = G.scene_setup(a, 0)
+    mos = np.stack([G.render_frame(a, 0, pos, xyz, col, cams, w2c) for pos in range(a.frames)])
+    got = dumps[0]
+    assert got["frame_index.npy"].tolist() == list(range(1, a.frames + 1))
+    sums = mos.reshape(a.frames, 2, a.height, 3, a.width, 3).sum(axis=(2, 4), dtype=np.int64)
+    assert np.array_equal(got["mosaic_cell_sums.npy"], sums.astype(np.float64))
+    at = got["mosaic_sample_index.npy"].astype(np.int64)
+    assert at.size == 1 << 21 and np.array_equal(got["mosaic_sample.npy"], mos.reshape(-1)[at].astype(np.float32))

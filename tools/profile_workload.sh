@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 R=$PWD
 o=$R/$o
-timeout 900 python bench.py "$@" > ${o}_bench.json 2> ${o}_bench.err
+timeout 900 python bench.py --full "$@" > ${o}_bench.json 2> ${o}_bench.err
 # (rocprofv3 runs from /tmp; --output-format csv: the default is a rocpd database; PMC passes carry --kernel-trace only)
 (cd /tmp && timeout 900 rocprofv3 --output-format csv --kernel-trace --stats -d ${o}_stats -o s -- python $R/bench.py "$@" --cpu-seconds 0 --sustain-seconds 0 > ${o}_stats.log 2>&1)
 (cd /tmp && env $penv timeout 900 rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d ${o}_pmc_fetch -o f -- python $R/tools/pmc_probe.py > ${o}_pmc_fetch.log 2>&1)

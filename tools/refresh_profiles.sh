@@ -16,14 +16,14 @@ tools/profile_workload.sh $tag scenes73 "N=10000 SCENES=73" --scenes 73 --steps 
 tools/profile_workload.sh $tag sites3x12 "N=1000000 MAP=site SITES=3 SCENES=12" --map site --verts 1000000 --sites 3 --scenes 12 --steps 10 --warmup 2 --cpu-seconds 0 > /dev/null
 # plain bench lines (no trace behind them)
 plain() { name=$1; shift; timeout 900 python bench.py "$@" > gpurun_out/${tag}_${name}_bench.json 2> gpurun_out/${tag}_${name}_bench.err; tail -c 300 gpurun_out/${tag}_${name}_bench.json; echo; }
-plain 960x540 --height 540 --width 960 --steps 60 --warmup 5
-plain n1e5 --verts 100000 --steps 30 --warmup 5
-plain dense1e6 --verts 1000000 --steps 20 --warmup 3
-plain site4e6 --map site --verts 4000000 --steps 20 --warmup 3
-plain segments --segments --steps 20 --warmup 5 --cpu-seconds 0
-plain wu --segments --wu --steps 20 --warmup 5 --cpu-seconds 0
+plain 960x540 --full --height 540 --width 960 --steps 60 --warmup 5
+plain n1e5 --full --verts 100000 --steps 30 --warmup 5
+plain dense1e6 --full --verts 1000000 --steps 20 --warmup 3
+plain site4e6 --full --map site --verts 4000000 --steps 20 --warmup 3
+plain segments --full --segments --steps 20 --warmup 5 --cpu-seconds 0
+plain wu --full --segments --wu --steps 20 --warmup 5 --cpu-seconds 0
 # N > 1 code path end to end on this one GPU (eight ranks share it, gloo for the one collective): functional, not a measurement
-CAMA_BENCH_SHARE_GPU=1 timeout 1500 python bench.py --gpus 8 --steps 2 --warmup 1 > gpurun_out/${tag}_8ranks_on_one_gpu_bench.json 2> gpurun_out/${tag}_8ranks_on_one_gpu_bench.err; tail -c 300 gpurun_out/${tag}_8ranks_on_one_gpu_bench.json; echo
+CAMA_BENCH_SHARE_GPU=1 plain 8ranks_on_one_gpu --full --gpus 8 --steps 2 --warmup 1
 # the reference's real workload: a fresh ClipManager per scene, both passes once (tools/cold_sweep.py)
 timeout 600 python tools/cold_sweep.py --scenes 12 --frames 40 --label final --json gpurun_out/${tag}_cold_final.json > gpurun_out/${tag}_cold_final.txt 2>&1
 CAMA_FRAME_CACHE_BYTES=0 timeout 600 python tools/cold_sweep.py --scenes 12 --frames 40 --label final_nocache --json gpurun_out/${tag}_cold_final_nocache.json > gpurun_out/${tag}_cold_final_nocache.txt 2>&1

@@ -4,7 +4,8 @@ set -u
 tag=$1; shift
 O=gpurun_out/smi_$tag.txt
 : > $O
-python bench.py "$@" --cpu-seconds 0 --sustain-seconds 6 > gpurun_out/smi_${tag}_bench.json 2>/dev/null &
+J=${O%.txt}_bench.json
+python bench.py --full "$@" --cpu-seconds 0 --sustain-seconds 6 > $J 2>/dev/null &
 pid=$!
 sleep 2
 while kill -0 $pid 2>/dev/null; do
